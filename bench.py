@@ -31,9 +31,15 @@ global batch is N*1024). C2's small table is replicated with one gradient
 all-reduce per step; C5's is row-sharded with the sparse exchange
 (KGE/sharded.py).
 
-Prints ONE JSON line (rank 0). The default C2 line at one GPU also carries
-roofline.hbm_point: the same step on a 50M-entity table, measured live
-(FB15k-237's table sits in the Infinity Cache; that one cannot).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps
+steps and prints the line (roofline and cpu_baseline null). ``--full`` adds the
+measurements that take runs of their own: the per-kernel HIP-event pass and
+the roofline against the spec and the measured copy peak, the CPU baseline,
+and, on the default C2 line at one GPU, roofline.hbm_point: the same step on a
+50M-entity table, measured live (FB15k-237's table sits in the Infinity Cache;
+that one cannot). ``--dump-outputs DIR`` writes what the last timed step
+computed (dump_outputs below); the inputs are seeded, so two builds run with
+the same arguments can be compared array for array.
 """
 
 import argparse
@@ -68,6 +74,7 @@ F32_MFMA_PEAK_TF = 157.3   # MI355X dense fp32 matrix peak (MI355X_MICROARCH.md)
 
 WORKLOADS = ("c2", "c1", "c3", "c4-rescal", "c4-transr", "c2-50m", "c5", "c1-train", "c2-train", "eval")
 F32_VALU_PEAK_TF = 157.3   # MI355X fp32 vector peak (MI355X_MICROARCH.md)
+DUMP_BYTES = 60_000_000    # --dump-outputs: array bytes in all (64 MB less room for the .npy headers)
 
 
 def parse():
@@ -79,10 +86,18 @@ def parse():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--neg", type=int, default=None)
     ap.add_argument("--dim", type=int, default=None)
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the per-kernel HIP-event pass, the roofline with the measured copy "
+                         "peak, roofline.hbm_point and the CPU baseline (a plain run times the steps and nothing else; "
+                         "its line carries roofline = cpu_baseline = null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="step workloads: after the timed steps write what the last one computed (its loss, the "
+                         "tables it updated) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: budget of the CPU baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-hbm-point", action="store_true",
-                    help="c2 at one GPU: skip the live C2-50M (HBM-honest) KS measurement in roofline.hbm_point")
+                    help="--full, c2 at one GPU: skip the live C2-50M (HBM-honest) KS measurement in "
+                         "roofline.hbm_point")
     ap.add_argument("--epochs", type=int, default=2, help="c1-train / c2-train: timed epochs (after one warm-up)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="one GPU: run the multi-GPU step (c5: all-to-all exchange + row cache instead of the "
@@ -93,7 +108,10 @@ def parse():
     ap.add_argument("--loopback", action="store_true",
                     help="with --force-exchange: every id (own ones too) through the exchange blocks -- the "
                          "remote path's kernels and copies on one GPU")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("c1-train", "c2-train", "eval"):
+        ap.error("--dump-outputs covers the step workloads (not %s)" % args.workload)
+    return args
 
 
 def load_graph():
@@ -590,7 +608,7 @@ def eval_leg(args, dev):
     dev_ms = sides["h"]["device_ms"] + sides["t"]["device_ms"]
     flops = 2 * n * E * d * 3.0
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the reference's per-triple get_rank loop restated on the host (torch CPU, same model)
         cm = TransE({"embedding_size": d}, w["K"], w["side"], score_fn=w["score"], loss_fn=w["loss"],
                     ns_strategy=UniformStrategy(np.arange(E), seed=1), constraint=w["constraint"])
@@ -698,14 +716,58 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        step(batches[args.warmup + s], True, opt)
+        loss = step(batches[args.warmup + s], True, opt)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     t1 = time.perf_counter()
     step.check_status()
     ms = (t1 - t0) * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, model, loss, sharded)   # (before any further step moves the tables)
 
+    k0 = ks = ku = None
+    if args.full:
+        k0, ks, ku = kernel_pass(args, step, batches, opt)
+    if sharded:
+        t = torch.tensor([ms], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        ms = float(t.item())
+    if rank != 0:
+        torch.distributed.destroy_process_group()
+        return
+
+    roof = cpu = None
+    if args.full:
+        roof = roofline(args, w, (B, K, d, E, R), batches, ms, (k0, ks, ku), dev, world)
+        if world == 1 and args.workload == "c2" and not args.no_cpu_baseline:
+            cpu = cpu_baseline(triples, E, R, B, K, d, args.cpu_seconds)
+    value = world * B / (ms * 1e-3)
+    out = {
+        "metric": "positive-triples/sec (batch x neg scored) at d=%d, %s" % (d, "FB15k-237" if not synthetic else
+                                                                              "synthetic %d entities" % E),
+        "value": round(value, 1), "unit": "positive-triples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms, 5), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32",
+        "data": ("synthetic %s ids over %d entities / %d relations; random-init weights"
+                 % ("Zipf" if w.get("zipf") else "uniform", E, R)) if synthetic
+        else "FB15k-237 train_indexed ids (real graph); random-init weights",
+        "config": {"workload": w["desc"] % dict(B=B, K=K, d=d, E=E), "global_batch": world * B,
+                   "negatives": K, "dim": d, "parallelism": "dp%d" % world,
+                   "scored_triples_per_s": round(value * (1 + K), 1)},
+        "roofline": roof, "cpu_baseline": cpu,
+    }
+    if sharded:
+        out["config"]["exchange"] = "local (one rank: fused step on the shard)" if step.direct is not None \
+            else step.mode + (" (loopback: every id through the blocks)" if args.loopback else "")
+    _RESULT_OUT.write(json.dumps(out) + "\n")
+    _RESULT_OUT.flush()
+    if sharded:
+        torch.distributed.destroy_process_group()
+
+
+def kernel_pass(args, step, batches, opt):
+    """--full: (K0, KS, KU) mean milliseconds of the step's kernel groups."""
     # per-kernel breakdown: a second pass over the same batches with HIP events
     # recorded on the step's own stream [before K0, before KS, after KS, after
     # the update kernels]; the events cost a few us per step, so this pass
@@ -724,14 +786,14 @@ def main():
     k0 = float(np.mean([r[0].elapsed_time(r[1]) for r in evs]))
     ks = float(np.mean([r[1].elapsed_time(r[2]) for r in evs]))
     ku = float(np.mean([r[2].elapsed_time(r[3]) for r in evs]))
-    if sharded:
-        t = torch.tensor([ms], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        ms = float(t.item())
-    if rank != 0:
-        torch.distributed.destroy_process_group()
-        return
+    return k0, ks, ku
 
+
+def roofline(args, w, dims, batches, ms, group, dev, world):
+    """--full: the line's roofline block from the step time, kernel_pass's
+    groups, the measured copy peak and (C2 at one GPU) the live hbm_point."""
+    B, K, d, E, R = dims
+    k0, ks, ku = group
     acc = accounting(w, B, K, d, E, R, batches[args.warmup])
     names = list(acc["kernels"])
     # event groups: KS group = the score pass (+ context / rank passes);
@@ -785,31 +847,31 @@ def main():
             and acc["bound"] == "hbm":
         roof["hbm_point"] = hbm_point(args, dev, R)
         roof["hbm_point"]["frac_measured"] = round(roof["hbm_point"]["achieved"] / roof["peak_measured"], 4)
-    cpu = None
-    if world == 1 and args.workload == "c2" and not args.no_cpu_baseline:
-        cpu = cpu_baseline(triples, E, R, B, K, d, args.cpu_seconds)
-    value = world * B / (ms * 1e-3)
-    out = {
-        "metric": "positive-triples/sec (batch x neg scored) at d=%d, %s" % (d, "FB15k-237" if not synthetic else
-                                                                              "synthetic %d entities" % E),
-        "value": round(value, 1), "unit": "positive-triples/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms, 5), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32",
-        "data": ("synthetic %s ids over %d entities / %d relations; random-init weights"
-                 % ("Zipf" if w.get("zipf") else "uniform", E, R)) if synthetic
-        else "FB15k-237 train_indexed ids (real graph); random-init weights",
-        "config": {"workload": w["desc"] % dict(B=B, K=K, d=d, E=E), "global_batch": world * B,
-                   "negatives": K, "dim": d, "parallelism": "dp%d" % world,
-                   "scored_triples_per_s": round(value * (1 + K), 1)},
-        "roofline": roof, "cpu_baseline": cpu,
-    }
+    return roof
+
+
+def dump_outputs(path, step, model, loss, sharded):
+    """--dump-outputs: what a caller of the timed step holds after its last
+    call -- the loss it returned and the tables it updated in place (a sharded
+    step: this rank's owned entity rows in place of the id-order table) -- as
+    path/<name>.npy, float32. Whole tables while they fit in DUMP_BYTES
+    together; else each table's share is a fixed sample of its rows (seeded
+    draw, ascending, the same rows in every run)."""
+    tables = dict(model.model_weights)
     if sharded:
-        out["config"]["exchange"] = "local (one rank: fused step on the shard)" if step.direct is not None \
-            else step.mode + (" (loopback: every id through the blocks)" if args.loopback else "")
-    _RESULT_OUT.write(json.dumps(out) + "\n")
-    _RESULT_OUT.flush()
-    if sharded:
-        torch.distributed.destroy_process_group()
+        tables.update(step.entity_parts())
+    tables = {k: v.detach().reshape(v.shape[0], -1) for k, v in tables.items() if v.numel()}
+    share = None
+    if sum(4 * v.numel() for v in tables.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // len(tables)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().reshape(-1).to(torch.float32).cpu().numpy())
+    for name, v in tables.items():
+        if share is not None and 4 * v.numel() > share:
+            g = torch.Generator().manual_seed(4242)
+            rows = torch.randint(0, v.shape[0], (max(1, share // (4 * v.shape[1])),), generator=g).sort().values
+            v = v[rows.to(v.device)]
+        np.save(os.path.join(path, name + ".npy"), v.to(torch.float32).cpu().numpy())
 
 
 if __name__ == "__main__":

@@ -19,11 +19,11 @@ rc=$?; echo "gpu suite: exit $rc"; grep -E "FAILED|ERROR|passed|failed" "$OUT/py
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { echo smoke failed; tail "$OUT/smoke.log"; exit 5; }
 cat "$OUT/smoke.log"
-timeout -k 10 300 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { echo "bench failed"; tail -20 "$OUT/bench_default.err"; exit 6; }
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { echo "bench failed"; tail -20 "$OUT/bench_default.err"; exit 6; }
 head -c 600 "$OUT/bench_default.json"; echo
 for a in "$@"; do
   tag=$(echo $a | tr ' ' '_' | tr -d '-')
-  timeout -k 10 300 python3 bench.py --workload $a --no-cpu-baseline --no-hbm-point > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" \
+  timeout -k 10 300 python3 bench.py --full --workload $a --no-cpu-baseline --no-hbm-point > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" \
     || { echo "bench $a failed"; tail -20 "$OUT/bench_$tag.err"; exit 7; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[1], d['ms_per_step'], r.get('kernel'), r.get('achieved'), r.get('frac'), r.get('frac_measured'))" "$OUT/bench_$tag.json"
 done

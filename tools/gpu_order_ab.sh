@@ -12,7 +12,7 @@ for rep in 1 2; do
   for leg in c4-rescal c4-transr; do
     for v in order batch; do
       if [ $v = batch ]; then export KGE_NO_POS_ORDER=1; else unset KGE_NO_POS_ORDER; fi
-      timeout -k 10 200 python3 bench.py --workload $leg --no-cpu-baseline > "$OUT/bench_${leg}_${v}_$rep.json" 2> "$OUT/err_$leg.txt" \
+      timeout -k 10 200 python3 bench.py --full --workload $leg --no-cpu-baseline > "$OUT/bench_${leg}_${v}_$rep.json" 2> "$OUT/err_$leg.txt" \
         || { echo "bench $leg $v failed"; tail -5 "$OUT/err_$leg.txt"; exit 3; }
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], sys.argv[3], d['ms_per_step'])" \
         "$OUT/bench_${leg}_${v}_$rep.json" $leg $v
@@ -22,7 +22,7 @@ done
 unset KGE_NO_POS_ORDER
 for leg in c4-rescal c4-transr; do
   timeout -s KILL 200 rocprofv3 --kernel-trace --stats -d "$OUT/trace_$leg" -o run --output-format csv -- \
-    python3 bench.py --workload $leg --steps 50 --warmup 10 --no-cpu-baseline > /dev/null 2> "$OUT/trace_$leg.err" \
+    python3 bench.py --full --workload $leg --steps 50 --warmup 10 --no-cpu-baseline > /dev/null 2> "$OUT/trace_$leg.err" \
     || { echo "trace failed"; tail -5 "$OUT/trace_$leg.err"; exit 3; }
   find "$OUT/trace_$leg" -name "*kernel_stats.csv" -exec cp {} "$OUT/${leg}_kernel_stats.csv" \;
   cut -c1-120 "$OUT/${leg}_kernel_stats.csv" | head -6

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 run() {   # run <dir> <leg> <counters...>
   local d=$1 w=$2; shift 2
   timeout -s KILL 120 rocprofv3 --pmc "$@" -d "$OUT/$d" -o run --output-format csv -- \
-    python3 bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-hbm-point > /dev/null 2> "$OUT/$d.err" \
+    python3 bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-hbm-point > /dev/null 2> "$OUT/$d.err" \
     || { echo "pmc $d failed"; tail -5 "$OUT/$d.err"; exit 3; }
 }
 for w in "$@"; do

@@ -5,17 +5,17 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export TMPDIR=/tmp
 OUT=gpurun_out/$1
 mkdir -p "$OUT"
-timeout -k 10 300 python3 bench.py --workload eval --no-cpu-baseline > "$OUT/bench_eval.json" 2> "$OUT/bench_eval.err" \
+timeout -k 10 300 python3 bench.py --full --workload eval --no-cpu-baseline > "$OUT/bench_eval.json" 2> "$OUT/bench_eval.err" \
   || { echo "eval failed"; tail -5 "$OUT/bench_eval.err"; exit 3; }
 cat "$OUT/bench_eval.json"
 timeout -s KILL 200 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
-  python3 bench.py --workload eval --no-cpu-baseline > /dev/null 2> "$OUT/trace.err" \
+  python3 bench.py --full --workload eval --no-cpu-baseline > /dev/null 2> "$OUT/trace.err" \
   || { echo "trace failed"; tail -5 "$OUT/trace.err"; exit 3; }
 cp "$OUT"/trace/run_kernel_stats.csv "$OUT/eval_kernel_stats.csv" 2>/dev/null || find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/eval_kernel_stats.csv" \;
 cut -c1-140 "$OUT/eval_kernel_stats.csv" | head -8
 timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES \
   -d "$OUT/pmc" -o run --output-format csv -- \
-  python3 bench.py --workload eval --no-cpu-baseline > /dev/null 2> "$OUT/pmc.err" \
+  python3 bench.py --full --workload eval --no-cpu-baseline > /dev/null 2> "$OUT/pmc.err" \
   || { echo "pmc failed"; tail -5 "$OUT/pmc.err"; exit 3; }
 python3 - "$OUT" <<'PY' | tee "$OUT/rank_sq.txt"
 import csv, glob, sys

@@ -7,7 +7,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 bash tools/gpu_tests.sh "$TAG" || exit 2
-timeout -k 10 300 python -u bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { echo "bench failed"; tail -20 "$OUT/bench_default.err"; exit 3; }
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { echo "bench failed"; tail -20 "$OUT/bench_default.err"; exit 3; }
 cat "$OUT/bench_default.json"
 if [ $# -gt 0 ]; then
   timeout -k 10 400 python -u tools/variants.py run "$@" > "$OUT/variants_c2.txt" 2>&1 || { echo "variants c2 failed"; cat "$OUT/variants_c2.txt"; exit 4; }

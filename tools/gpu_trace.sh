@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for a in "$@"; do
   tag=$(echo $a | tr ' ' '_' | tr -d '-')
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$tag" -o run --output-format csv -- \
-    python3 bench.py --workload $a --steps 30 --warmup 5 --no-cpu-baseline --no-hbm-point \
+    python3 bench.py --full --workload $a --steps 30 --warmup 5 --no-cpu-baseline --no-hbm-point \
     > "$OUT/bench_$tag.json" 2> "$OUT/prof_$tag.err" || { echo "rocprof $a failed"; tail -20 "$OUT/prof_$tag.err"; exit 4; }
   f=$(find "$OUT/prof_$tag" -name "*kernel_trace.csv" | head -1)
   python3 tools/kgaps.py "$f" > "$OUT/gaps_$tag.txt"

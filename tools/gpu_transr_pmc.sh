@@ -11,7 +11,7 @@ for v in v2 v1; do
   if [ $v = v1 ]; then export KGE_TRANSR_V1=1; fi
   timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE \
     -d "$OUT/pmc_$v" -o run --output-format csv -- \
-    python3 bench.py --workload c4-transr --steps 10 --warmup 3 --no-cpu-baseline --no-hbm-point > /dev/null 2> "$OUT/pmc_$v.err" \
+    python3 bench.py --full --workload c4-transr --steps 10 --warmup 3 --no-cpu-baseline --no-hbm-point > /dev/null 2> "$OUT/pmc_$v.err" \
     || { echo "pmc $v failed"; tail -5 "$OUT/pmc_$v.err"; exit 3; }
   python3 - "$OUT/pmc_$v/run_counter_collection.csv" <<'PY'
 import csv, sys

@@ -9,7 +9,7 @@ timeout -k 10 500 python3 -u -m pytest tests/test_gpu_step.py -x -q -m gpu -k "t
   --timeout 120 --timeout-method thread > "$OUT/pytest_transr.log" 2>&1 || { echo "tests failed"; tail -30 "$OUT/pytest_transr.log"; exit 3; }
 tail -1 "$OUT/pytest_transr.log"
 for rep in 1 2; do
-  timeout -k 10 200 python3 bench.py --workload c4-transr --no-cpu-baseline > "$OUT/bench_c4-transr_$rep.json" 2> "$OUT/err.txt" \
+  timeout -k 10 200 python3 bench.py --full --workload c4-transr --no-cpu-baseline > "$OUT/bench_c4-transr_$rep.json" 2> "$OUT/err.txt" \
     || { echo "bench failed"; tail -5 "$OUT/err.txt"; exit 3; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('c4-transr', d['ms_per_step'])" "$OUT/bench_c4-transr_$rep.json"
 done

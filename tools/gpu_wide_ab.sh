@@ -6,7 +6,7 @@ OUT=gpurun_out/$1; shift
 mkdir -p "$OUT"
 for rep in 1 2; do
   for leg in c3 c5; do
-    timeout -k 10 200 python3 bench.py --workload $leg --no-cpu-baseline --no-hbm-point > "$OUT/base_${leg}_$rep.json" 2>/dev/null || exit 3
+    timeout -k 10 200 python3 bench.py --full --workload $leg --no-cpu-baseline --no-hbm-point > "$OUT/base_${leg}_$rep.json" 2>/dev/null || exit 3
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); k=d['roofline'].get('kernels') or {}; print('base', sys.argv[2], d['ms_per_step'], k)" "$OUT/base_${leg}_$rep.json" $leg
     timeout -k 10 600 python3 tools/variants.py run "$@" -- --workload $leg || exit 3
   done
