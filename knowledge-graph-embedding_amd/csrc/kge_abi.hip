@@ -1080,9 +1080,14 @@ kge_status kge_rank(const kge_rank_desc* d, void* stream) {
   A.pos = d->pos_score_out;
   A.status = d->status;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipMemsetAsync(d->rank_out, 0, (size_t)d->n * sizeof(int64_t), st);
+  // the count passes add into rank_out: a failed clear is an error, not stale counts
+  const hipError_t me = hipMemsetAsync(d->rank_out, 0, (size_t)d->n * sizeof(int64_t), st);
+  if (me != hipSuccess) return fail(KGE_EHIP, "kge_rank: clearing rank_out: %s", hipGetErrorString(me));
   const int sk = d->score_kind == KGE_SCORE_DOT ? SK_DOT : score_sk(d->score_kind, p);
-  if (launch_rank(A, d->mode, d->proj, sk, st) != KGE_OK)
+  const kge_status ls = launch_rank(A, d->mode, d->proj, sk, st);
+  if (ls == KGE_EHIP)
+    return fail(KGE_EHIP, "kge_rank: clearing the filter bitmap: %s", hipGetErrorString(hipGetLastError()));
+  if (ls != KGE_OK)
     return fail(KGE_EUNSUPPORTED, "no ranking instance for mode %d / score %d", d->mode, d->score_kind);
   return hip_check("kge_rank");
 }

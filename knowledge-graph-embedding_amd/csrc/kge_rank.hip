@@ -517,7 +517,8 @@ kge_status launch_rank(const RankArgs& A, int mode, int proj, int sk, hipStream_
     if (A.fw <= kBitsLds) {
       hipLaunchKernelGGL(rank_bits_kernel<true>, dim3((unsigned)A.n), dim3(256), 0, st, A, bits);
     } else {
-      (void)hipMemsetAsync(bits, 0, (size_t)(A.n * A.fw) * sizeof(uint32_t), st);
+      // a failed clear would leave the caller's stale words as filter bits
+      if (hipMemsetAsync(bits, 0, (size_t)(A.n * A.fw) * sizeof(uint32_t), st) != hipSuccess) return KGE_EHIP;
       hipLaunchKernelGGL(rank_bits_kernel<false>, dim3((unsigned)A.n), dim3(256), 0, st, A, bits);
     }
   }

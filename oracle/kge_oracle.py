@@ -307,8 +307,10 @@ def filtered_ranks(model, weights, X, side, positive_X=None, score=("lp", 2.0), 
     None), the known positives sharing the query's (r, kept entity) set to
     -inf (:646-650), rank = 1 + #(scores > the true triple's score) (:652-654;
     counted in int64, the reference's int16 overflows past 32,767).
-    Also returns, per query, the candidates within tie_tol * max(1, |s_true|)
-    of the true score: an fp32 evaluation may order those either way."""
+    Also returns, per query, the number of candidates -- other than the true
+    entity and the filtered ones, which no rank counts -- within
+    tie_tol * max(1, |s_true|) of the true score: an fp32 evaluation may order
+    those either way, so its rank may differ by at most that many (0: equal)."""
     W = {k: torch.tensor(np.asarray(v), dtype=F64) for k, v in weights.items()}
     L = _Lookups(W, False)
     cfg = {"constraint": constraint, "constraint_weight": 1.0, "limit": limit}
@@ -323,13 +325,17 @@ def filtered_ranks(model, weights, X, side, positive_X=None, score=("lp", 2.0), 
             h = every if side == "h" else np.full(E, x[0])
             t = every if side == "t" else np.full(E, x[2])
             s = _score_hrt(model, W, L, h, np.full(E, x[1]), t, score, cfg).numpy().copy()
-            ps = float(_score_hrt(model, W, L, x[0:1], x[1:2], x[2:3], score, cfg).reshape(-1)[0])
-            near = int(np.sum(np.abs(s - ps) <= tie_tol * max(1.0, abs(ps))))
+            # the true score from the same evaluation: a duplicate of the true
+            # row ties it exactly here, as it does bit for bit in the kernel
+            ps = float(s[x[corr]])
+            live = np.ones(E, dtype=bool)             # candidates a rank can still count:
+            live[x[corr]] = False                     # not the true entity itself,
             if P is not None:
                 m = (P[:, 1] == x[1]) & (P[:, keep] == x[keep])
                 s[P[m, corr]] = -np.inf
+                live[P[m, corr]] = False              # nor a filtered one
             ranks.append(int(np.sum(s > ps)) + 1)
-            ties.append(near)
+            ties.append(int(np.sum(live & (np.abs(s - ps) <= tie_tol * max(1.0, abs(ps))))))
     return np.array(ranks, dtype=np.int64), np.array(ties, dtype=np.int64)
 
 

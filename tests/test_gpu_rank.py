@@ -1,9 +1,10 @@
 """GPU: batched filtered ranking (kge_rank, csrc/kge_rank.hip) vs the
 reference's per-triple get_rank (BaseModel.py:620-654) restated in torch on
-the same weights. Ranks are integers; they must be equal except where the
-per-triple path's own scores tie the true triple's within fp32 rounding
-(|s_e - s_true| <= 1e-5 max(1, |s_true|)), where a rank may move by at most
-the number of such near-ties."""
+the same weights. Ranks are integers; they must be equal except where another
+countable candidate (not the true entity, not filtered) scores within fp32
+rounding of the true triple (|s_e - s_true| <= 1e-5 max(1, |s_true|)), where
+a rank may move by at most the number of such near-ties. Exact comparisons on
+integer inputs are in test_gpu_rank_exact.py."""
 
 import os
 
@@ -25,15 +26,24 @@ def _fused(monkeypatch, hiplib):
 
 
 def _per_triple(m, X, side, positive_X):
-    """Reference loop: ranks and the near-tie count of each query."""
+    """Reference loop: ranks and the near-tie count of each query -- the
+    candidates other than the true entity and the filtered ones (no rank counts
+    those) within the tolerance of the true score, taken from the same
+    all-candidates evaluation (oracle.filtered_ranks' rule)."""
     ranks, ties = [], []
+    keep, corr = (2, 0) if side == "h" else (0, 2)
+    P = None if positive_X is None else np.asarray(positive_X).reshape(-1, 3)
     for x in X:
         ranks.append(int(m.get_rank(x, positive_X, side)))
         with torch.no_grad():
             s = (m.score_hrt(h=None, r=x[1], t=x[2]) if side == "h" else m.score_hrt(h=x[0], r=x[1], t=None))
-            s = s.reshape(-1).double()
-            p = m.score_hrt(x[0:1], x[1:2], x[2:3]).reshape(()).double()
-        ties.append(int(torch.sum(torch.abs(s - p) <= 1e-5 * max(1.0, abs(float(p)))).item()))
+            s = s.reshape(-1).double().cpu().numpy()
+        p = float(s[x[corr]])
+        live = np.ones(len(s), dtype=bool)
+        live[x[corr]] = False
+        if P is not None:
+            live[P[(P[:, 1] == x[1]) & (P[:, keep] == x[keep]), corr]] = False
+        ties.append(int(np.sum(live & (np.abs(s - p) <= 1e-5 * max(1.0, abs(p))))))
     return np.array(ranks), np.array(ties)
 
 
