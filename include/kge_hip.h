@@ -419,6 +419,63 @@ typedef struct kge_rank_desc {
 kge_status kge_rank(const kge_rank_desc* d, void* stream);
 
 /*
+ * Top-k link prediction: for each of the n queries (h, r, ?) / (?, r, t) the
+ * k best candidates of the corrupted side. The queries, the candidates, the
+ * score and the filter are given exactly as for kge_rank (q); the scores are
+ * computed by the same functions, op by op in the same order.
+ *   Selection and order: row q of the outputs holds the candidates e in [0, E)
+ *     that are not in filter(q), by score descending; equal scores (float ==,
+ *     so +0 and -0 tie) by ascending entity id. The first min(k, live(q))
+ *     entries are written, the remaining slots get id -1 and score -inf, and
+ *     count_out[q] is the number written.
+ *   NaN scores: a candidate whose score is NaN orders below every non-NaN
+ *     candidate (below -inf), NaNs among themselves by id -- as in kge_rank,
+ *     where a NaN never counts as above anything.
+ *   Score bits: scores_out holds the bits kge_rank writes to pos_score_out for
+ *     that entity (the sign of a zero included; a NaN comes back as the
+ *     canonical quiet NaN).
+ *   Ranks: a returned id fed back to kge_rank as true_ids with the same filter
+ *     has rank 1 + the number of entries of its row with a strictly greater
+ *     score.
+ *   Filter: the bitmap only. The call builds q.filt_bits from the filter lists
+ *     as kge_rank does and the producers skip the marked candidates; filt_beg
+ *     without filt_bits is KGE_EINVAL. A filter id outside [0, E) sets
+ *     KGE_ERANGE in the status word.
+ *   Validation: kge_rank's checks, less the three ignored pointers; k outside
+ *     1 .. KGE_TOPK_MAX_K, unknown flags, a non-zero q.flags, null outputs or
+ *     workspace are KGE_EINVAL, a workspace below kge_topk_workspace_bytes()
+ *     KGE_ENOMEM_WORKSPACE, E >= 2^31 - 1 KGE_EUNSUPPORTED (the entity id
+ *     shares a 64-bit sort key with the score).
+ *   n == 0 returns KGE_OK and touches nothing. The library allocates nothing;
+ *     a failed clear of the bitmap is KGE_EHIP. Stream-ordered.
+ * KGE_TOPK_FLAG_LANE_PASS forces the lane-per-candidate producer where the
+ * register-tiled one applies (TRANS without a projection, MUL, DOT, k <= 32);
+ * KGE_TOPK_FLAG_DEBUG_SLAB is a test hook: 256-candidate slabs, so the merge
+ * of per-slab lists runs at small E. Neither changes a bit of the outputs.
+ */
+enum { KGE_TOPK_MAX_K = 1024 };
+enum { KGE_TOPK_FLAG_LANE_PASS = 1, KGE_TOPK_FLAG_DEBUG_SLAB = 2 };
+
+typedef struct kge_topk_desc {
+  kge_rank_desc q;            /* as for kge_rank; q.true_ids / q.rank_out / q.pos_score_out
+                                 are ignored (may be NULL); q.flags must be 0; with a
+                                 filter, q.filt_bits is REQUIRED                 */
+  int32_t k;                  /* 1 .. KGE_TOPK_MAX_K                            */
+  int32_t flags;              /* KGE_TOPK_FLAG_*                                */
+  void* ids_out;              /* [n, k] q.idx_dtype                             */
+  float* scores_out;          /* [n, k]                                         */
+  int32_t* count_out;         /* [n] valid entries of each row (nullable)       */
+  void* workspace;            /* >= kge_topk_workspace_bytes(); contents on entry ignored */
+  uint64_t workspace_bytes;
+} kge_topk_desc;
+
+/* Workspace of a kge_topk call (a function of mode, proj, dim, n, E, k and
+ * flags); 0 if the descriptor is invalid. */
+uint64_t kge_topk_workspace_bytes(const kge_topk_desc* d);
+/* Top-k link prediction (see kge_topk_desc). */
+kge_status kge_topk(const kge_topk_desc* d, void* stream);
+
+/*
  * Sparse SGD apply of one variable on listed rows (the owner-side update of
  * the multi-GPU step, KGE/sharded.py): for i < n,
  *   var[rows[i]] += -lr * clip_norm / max(sqrt(*norm2), clip_norm) * grad[i]

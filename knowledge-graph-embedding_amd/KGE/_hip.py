@@ -107,6 +107,16 @@ class kge_rank_desc(ctypes.Structure):
                 ("filt_bits_words", ctypes.c_int64)]
 
 
+TOPK_MAX_K = 1024
+TOPK_FLAG_LANE_PASS, TOPK_FLAG_DEBUG_SLAB = 1, 2
+
+
+class kge_topk_desc(ctypes.Structure):
+    _fields_ = [("q", kge_rank_desc), ("k", ctypes.c_int32), ("flags", ctypes.c_int32), ("ids_out", ctypes.c_void_p),
+                ("scores_out", ctypes.c_void_p), ("count_out", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_uint64)]
+
+
 class kge_apply_rows_desc(ctypes.Structure):
     _fields_ = [("var", kge_table), ("rows", ctypes.c_void_p), ("n", ctypes.c_int64), ("grad", ctypes.c_void_p),
                 ("grad_ld", ctypes.c_int64), ("norm2", ctypes.c_void_p), ("lr", ctypes.c_float),
@@ -145,7 +155,8 @@ class kge_stream_desc(ctypes.Structure):
 
 EXPORTS = ("kge_abi_version", "kge_last_error", "kge_step_workspace_bytes", "kge_step_plan_signature", "kge_step",
            "kge_sample",
-           "kge_apply", "kge_apply_many", "kge_constrain_rows", "kge_rank", "kge_apply_rows", "kge_stream_batch",
+           "kge_apply", "kge_apply_many", "kge_constrain_rows", "kge_rank", "kge_topk_workspace_bytes", "kge_topk",
+           "kge_apply_rows", "kge_stream_batch",
            "kge_stream_permutation", "kge_stream_batch_perm", "kge_exchange_plan",
            "kge_exchange_rows", "kge_owner_record_floats", "kge_histogram", "kge_copy16")
 
@@ -184,6 +195,10 @@ def load(path=LIB_PATH):
         L.kge_apply_rows.argtypes = [ctypes.POINTER(kge_apply_rows_desc), ctypes.c_void_p]
         L.kge_rank.restype = ctypes.c_int
         L.kge_rank.argtypes = [ctypes.POINTER(kge_rank_desc), ctypes.c_void_p]
+        L.kge_topk_workspace_bytes.restype = ctypes.c_uint64
+        L.kge_topk_workspace_bytes.argtypes = [ctypes.POINTER(kge_topk_desc)]
+        L.kge_topk.restype = ctypes.c_int
+        L.kge_topk.argtypes = [ctypes.POINTER(kge_topk_desc), ctypes.c_void_p]
         L.kge_stream_batch.restype = ctypes.c_int
         L.kge_stream_batch.argtypes = [ctypes.POINTER(kge_stream_desc), ctypes.c_void_p]
         L.kge_stream_permutation.restype = ctypes.c_int

@@ -709,6 +709,54 @@ class KGEModel:
             pos_score = self.score_hrt(x[0:1], x[1:2], x[2:3]).reshape(())
             return np.int64(int(torch.sum(scores > pos_score).item()) + 1)
 
+    def predict(self, X, corrupt_side, k=10, positive_X=None):
+        """Link prediction: for every row of ``X`` ([n, 3]; the corrupted
+        side's column is ignored and may hold anything) the ``k`` best-scoring
+        entities on that side, ``(ids int64 [n, k], scores float32 [n, k])`` as
+        numpy arrays. Best first, equal scores by ascending entity id, a NaN
+        score after every other; the known positives of ``positive_X`` sharing
+        the query's (relation, kept entity) are left out, as ``get_rank``
+        filters them. A row with fewer than ``k`` live entities ends in id -1 /
+        score -inf.
+
+        The built-in models with built-in scores on the GPU go through
+        ``kge_topk`` (``ranking.batched_topk``) for ``k <= KGE_TOPK_MAX_K``;
+        everything else (UM, SE, subclasses, custom scores, CPU tensors, the
+        eager backend, larger ``k``) sorts ``score_hrt``'s scores per query."""
+        if corrupt_side not in ("h", "t"):
+            raise ValueError("corrupt_side must be 'h' or 't'")
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        X = np.asarray(X.cpu() if isinstance(X, torch.Tensor) else X).reshape(-1, 3)
+        from ... import _hip, engine, ranking
+        if engine.backend() != "eager" and ranking.supported(self) and k <= _hip.TOPK_MAX_K:
+            return ranking.batched_topk(self, X, corrupt_side, k, positive_X)
+        ids = np.full((len(X), k), -1, dtype=np.int64)
+        scores = np.full((len(X), k), -np.inf, dtype=np.float32)
+        keep, corrupt = (2, 0) if corrupt_side == "h" else (0, 2)
+        P = None
+        if positive_X is not None:
+            P = np.asarray(positive_X.cpu() if isinstance(positive_X, torch.Tensor) else positive_X).reshape(-1, 3)
+        for i, x in enumerate(X):
+            with torch.no_grad():
+                if corrupt_side == "h":
+                    s = self.score_hrt(h=None, r=x[1], t=x[2])
+                else:
+                    s = self.score_hrt(h=x[0], r=x[1], t=None)
+            s = s.reshape(-1).to(torch.float32).cpu().numpy()
+            live = np.ones(len(s), dtype=bool)
+            if P is not None:
+                live[P[(P[:, 1] == x[1]) & (P[:, keep] == x[keep]), corrupt].astype(np.int64)] = False
+            cand = np.nonzero(live)[0]
+            v = s[cand]
+            nan = np.isnan(v)
+            # NaNs last, then score descending (+0 == -0), then ascending id
+            order = np.lexsort((cand, -np.where(nan, 0, v), nan))[:k]
+            ids[i, :len(order)] = cand[order]
+            scores[i, :len(order)] = v[order]
+        return ids, scores
+
     def restore_model_weights(self, model_weights):
         """``BaseModel.py:656-666`` (argument checked)."""
         self._check_model_weights(model_weights)

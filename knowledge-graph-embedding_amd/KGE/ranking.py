@@ -9,6 +9,10 @@ the model's own op order (below, one builder per built-in model), builds the
 filter as a sorted (relation, kept entity) -> entity index, and the HIP
 kernels score all E candidates of every query (``csrc/kge_rank.hip``).
 
+``batched_topk`` answers the open question instead -- the k best entities of
+every query -- through ``kge_topk`` (``csrc/kge_topk.hip``) with the same row
+builders and filter index.
+
 Only the exact built-in model classes with built-in score functions take
 this path; user subclasses, UM / SE and custom scores keep the reference's
 per-triple loop (``BaseModel.get_rank``).
@@ -375,3 +379,87 @@ def batched_ranks(model, eval_X, corrupt_side, positive_X=None, flags=0):
         keep.append((q0, q1, qw, ids, rk, ps, g["cand"]))
     _hip.check_device_status(status, "kge_rank")
     return ranks.cpu().numpy()
+
+
+def batched_topk(model, X, corrupt_side, k, positive_X=None, flags=0):
+    """The ``k`` best entities of every query of ``X`` ([n, 3]; the corrupted
+    side's column is ignored) through ``kge_topk``: ``(ids int64 [n, k],
+    scores float32 [n, k])`` as numpy arrays, best first, equal scores by
+    ascending id, the known positives of ``positive_X`` left out; rows with
+    fewer than ``k`` live entities end in id -1 / score -inf.
+    ``flags``: KGE_TOPK_FLAG_*."""
+    if corrupt_side not in ("h", "t"):
+        raise ValueError("corrupt_side must be 'h' or 't'")
+    lib = _hip.lib()
+    dev = model.model_weights["ent_emb"].device
+    X = torch.as_tensor(np.asarray(X.cpu() if isinstance(X, torch.Tensor) else X),
+                        dtype=torch.int64).to(dev).reshape(-1, 3).clone()
+    X[:, 0 if corrupt_side == "h" else 2] = 0     # ignored: may hold anything, the builders look rows up by it
+    n = X.shape[0]
+    k = int(k)
+    E = int(model.model_weights["ent_emb"].shape[0])
+    ids = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    scores = torch.full((n, k), float("-inf"), dtype=torch.float32, device=dev)
+    if n == 0:
+        return ids.cpu().numpy(), scores.cpu().numpy()
+    h, r, t = X[:, 0], X[:, 1], X[:, 2]
+    with torch.no_grad():
+        groups = _builders()[type(model)](model, h, r, t, corrupt_side)
+    if groups is None:
+        raise NotImplementedError("no batched ranking for this model / score")
+    if positive_X is not None:
+        fkeys, fent = cached_filter_keys(positive_X, corrupt_side, E, dev)
+        fb, fe = filter_lookup(X, fkeys, fent, corrupt_side, E)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    # the filter is the bitmap only (no rescoring pass to drop to): the queries
+    # go in chunks whose n x ceil(E / 32) words stay under _BITS_MAX_BYTES
+    W = (E + 31) // 32
+    step = max(1, _BITS_MAX_BYTES // (W * 4)) if positive_X is not None else n
+    for g in groups:
+        sel = g["sel"]
+        m = n if sel is None else int(sel.shape[0])
+        q0 = g["q0"].to(torch.float32).contiguous()
+        q1 = g["q1"].to(torch.float32).contiguous() if g["q1"] is not None else None
+        qw = g["qw"].to(torch.float32).contiguous() if g["qw"] is not None else None
+        gi = ids if sel is None else torch.empty((m, k), dtype=torch.int64, device=dev)
+        gs = scores if sel is None else torch.empty((m, k), dtype=torch.float32, device=dev)
+        if positive_X is not None:
+            gb = fb if sel is None else fb[sel].contiguous()
+            ge = fe if sel is None else fe[sel].contiguous()
+        bits = torch.empty(min(m, step) * W, dtype=torch.int32, device=dev) if positive_X is not None else None
+        ws = None
+        for c0 in range(0, m, step):
+            c = min(step, m - c0)
+            d = _hip.kge_topk_desc()
+            d.q.abi_version = _hip.ABI_VERSION
+            d.q.mode = g["mode"]
+            d.q.proj = g["proj"]
+            d.q.corrupt_side = _hip.SIDE_H if corrupt_side == "h" else _hip.SIDE_T
+            d.q.cand = _hip.table(g["cand"])
+            if g["cand_aux"] is not None:
+                d.q.cand_aux = _hip.table(g["cand_aux"])
+            d.q.dim = g["dim"]
+            d.q.clip = g["clip"]
+            d.q.q0 = q0[c0:].data_ptr()
+            d.q.q1 = q1[c0:].data_ptr() if q1 is not None else None
+            d.q.qw = qw[c0:].data_ptr() if qw is not None else None
+            d.q.ldq = q0.shape[1]
+            d.q.idx_dtype = _hip.IDX_I64
+            d.q.score_kind, d.q.score_p = g["score"]
+            d.q.n = c
+            if positive_X is not None:
+                d.q.filt_beg, d.q.filt_end, d.q.filt_ent = gb[c0:].data_ptr(), ge[c0:].data_ptr(), fent.data_ptr()
+                d.q.filt_bits, d.q.filt_bits_words = bits.data_ptr(), bits.numel()
+            d.q.status = status.data_ptr()
+            d.k, d.flags = k, int(flags)
+            d.ids_out, d.scores_out = gi[c0:].data_ptr(), gs[c0:].data_ptr()
+            need = int(lib.kge_topk_workspace_bytes(ctypes.byref(d)))
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+            _hip.check(lib.kge_topk(ctypes.byref(d), _hip.stream_handle(dev)), "kge_topk")
+        if sel is not None:
+            ids[sel] = gi
+            scores[sel] = gs
+    _hip.check_device_status(status, "kge_topk")
+    return ids.cpu().numpy(), scores.cpu().numpy()

@@ -1013,8 +1013,11 @@ kge_status kge_sample(const kge_sample_desc* d, void* stream) {
   return hip_check("kge_sample");
 }
 
-kge_status kge_rank(const kge_rank_desc* d, void* stream) {
-  if (!d) return fail(KGE_EINVAL, "null descriptor");
+// kge_rank's descriptor checks and launch arguments, shared with kge_topk
+// (topk: true_ids / rank_out / pos_score_out are not needed and flags must be
+// 0). *empty: n == 0, nothing to do.
+static kge_status rank_args(const kge_rank_desc* d, bool topk, RankArgs& A, bool* empty) {
+  *empty = false;
   if (d->abi_version != KGE_ABI_VERSION)
     return fail(KGE_EINVAL, "abi_version %d != library %d", d->abi_version, KGE_ABI_VERSION);
   if (d->mode < KGE_RANK_TRANS || d->mode > KGE_RANK_DOT) return fail(KGE_EINVAL, "unknown rank mode %d", d->mode);
@@ -1023,9 +1026,9 @@ kge_status kge_rank(const kge_rank_desc* d, void* stream) {
   if (d->corrupt_side != KGE_SIDE_H && d->corrupt_side != KGE_SIDE_T)
     return fail(KGE_EINVAL, "corrupt_side must be 'h' or 't'");
   if (d->n < 0) return fail(KGE_EINVAL, "n must be >= 0");
-  if (d->n == 0) return KGE_OK;
+  if (d->n == 0) { *empty = true; return KGE_OK; }
   if (!d->cand.data || d->cand.rows <= 0 || d->cand.ld < d->cand.cols) return fail(KGE_EINVAL, "bad candidate table");
-  if (d->dim <= 0 || !d->q0 || d->ldq < d->dim || !d->true_ids || !d->rank_out || !d->pos_score_out)
+  if (d->dim <= 0 || !d->q0 || d->ldq < d->dim || (!topk && (!d->true_ids || !d->rank_out || !d->pos_score_out)))
     return fail(KGE_EINVAL, "null query rows / ids / outputs");
   const bool hside = d->corrupt_side == KGE_SIDE_H;
   const bool rank1 = d->proj == KGE_RPROJ_RANK1, hyper = d->proj == KGE_RPROJ_HYPER;
@@ -1043,7 +1046,6 @@ kge_status kge_rank(const kge_rank_desc* d, void* stream) {
   if (d->score_kind != KGE_SCORE_DOT && !(p > 0.f))
     return fail(KGE_EINVAL, "Lp score needs p > 0 (got %g)", (double)p);
   if (3 * kRankQ * ((d->dim + 3) & ~3) * 4 > 64 * 1024) return fail(KGE_EUNSUPPORTED, "query rows too wide");
-  RankArgs A{};
   A.cand = d->cand.data;
   A.cand_ld = d->cand.ld;
   A.E = d->cand.rows;
@@ -1063,11 +1065,13 @@ kge_status kge_rank(const kge_rank_desc* d, void* stream) {
   A.true_ids = d->true_ids;
   A.i64 = d->idx_dtype == KGE_IDX_I64;
   A.n = d->n;
-  if (d->flags & ~KGE_RANK_FLAG_LANE_PASS) return fail(KGE_EINVAL, "kge_rank: unknown flags 0x%x", d->flags);
+  if (topk ? d->flags != 0 : (d->flags & ~KGE_RANK_FLAG_LANE_PASS) != 0)
+    return fail(KGE_EINVAL, "%s: unknown flags 0x%x", topk ? "kge_topk: q.flags must be 0" : "kge_rank", d->flags);
   A.lane_pass = (d->flags & KGE_RANK_FLAG_LANE_PASS) != 0;
   A.fbeg = d->filt_beg;
   A.fend = d->filt_end;
   A.fent = d->filt_ent;
+  if (topk && d->filt_beg && !d->filt_bits) return fail(KGE_EINVAL, "kge_topk: a filter needs q.filt_bits");
   if (d->filt_bits && d->filt_beg) {   // (no filter: the bitmap is ignored)
     A.fw = (A.E + 31) / 32;
     if (d->filt_bits_words < d->n * A.fw)
@@ -1079,17 +1083,82 @@ kge_status kge_rank(const kge_rank_desc* d, void* stream) {
   A.rank = (unsigned long long*)d->rank_out;
   A.pos = d->pos_score_out;
   A.status = d->status;
+  return KGE_OK;
+}
+
+kge_status kge_rank(const kge_rank_desc* d, void* stream) {
+  if (!d) return fail(KGE_EINVAL, "null descriptor");
+  RankArgs A{};
+  bool empty;
+  const kge_status vs = rank_args(d, false, A, &empty);
+  if (vs != KGE_OK || empty) return vs;
   hipStream_t st = (hipStream_t)stream;
   // the count passes add into rank_out: a failed clear is an error, not stale counts
   const hipError_t me = hipMemsetAsync(d->rank_out, 0, (size_t)d->n * sizeof(int64_t), st);
   if (me != hipSuccess) return fail(KGE_EHIP, "kge_rank: clearing rank_out: %s", hipGetErrorString(me));
-  const int sk = d->score_kind == KGE_SCORE_DOT ? SK_DOT : score_sk(d->score_kind, p);
+  const int sk = d->score_kind == KGE_SCORE_DOT ? SK_DOT : score_sk(d->score_kind, d->score_p);
   const kge_status ls = launch_rank(A, d->mode, d->proj, sk, st);
   if (ls == KGE_EHIP)
     return fail(KGE_EHIP, "kge_rank: clearing the filter bitmap: %s", hipGetErrorString(hipGetLastError()));
   if (ls != KGE_OK)
     return fail(KGE_EUNSUPPORTED, "no ranking instance for mode %d / score %d", d->mode, d->score_kind);
   return hip_check("kge_rank");
+}
+
+// kge_topk's checks; fills the launch arguments and the plan. *empty: n == 0.
+static kge_status topk_args(const kge_topk_desc* d, RankArgs& A, TopkArgs& T, TopkPlan& P, uint64_t* need, bool* empty) {
+  *need = 0;
+  const kge_status vs = rank_args(&d->q, true, A, empty);
+  if (vs != KGE_OK) return vs;
+  if (d->k < 1 || d->k > KGE_TOPK_MAX_K) return fail(KGE_EINVAL, "kge_topk: k = %d outside 1 .. %d", d->k, KGE_TOPK_MAX_K);
+  if (d->flags & ~(KGE_TOPK_FLAG_LANE_PASS | KGE_TOPK_FLAG_DEBUG_SLAB))
+    return fail(KGE_EINVAL, "kge_topk: unknown flags 0x%x", d->flags);
+  if (*empty) return KGE_OK;
+  if (A.E >= 0x7fffffffLL) return fail(KGE_EUNSUPPORTED, "kge_topk: more than 2^31 - 2 candidates");
+  if (d->q.mode == KGE_RANK_ROT && d->q.score_kind == KGE_SCORE_DOT)
+    return fail(KGE_EUNSUPPORTED, "no ranking instance for mode %d / score %d", d->q.mode, d->q.score_kind);
+  P = topk_plan(d->q.mode, d->q.proj, d->q.dim, d->q.n, A.E, d->k, d->flags);
+  *need = (uint64_t)d->q.n * (uint64_t)P.nslab * (uint64_t)d->k * sizeof(uint64_t);
+  T.k = d->k;
+  T.out64 = A.i64;
+  T.ids = d->ids_out;
+  T.scores = d->scores_out;
+  T.count = d->count_out;
+  T.lists = (unsigned long long*)d->workspace;
+  return KGE_OK;
+}
+
+uint64_t kge_topk_workspace_bytes(const kge_topk_desc* d) {
+  if (!d) return 0;
+  RankArgs A{};
+  TopkArgs T{};
+  TopkPlan P{};
+  uint64_t need;
+  bool empty;
+  if (topk_args(d, A, T, P, &need, &empty) != KGE_OK) return 0;
+  return need;
+}
+
+kge_status kge_topk(const kge_topk_desc* d, void* stream) {
+  if (!d) return fail(KGE_EINVAL, "null descriptor");
+  RankArgs A{};
+  TopkArgs T{};
+  TopkPlan P{};
+  uint64_t need;
+  bool empty;
+  const kge_status vs = topk_args(d, A, T, P, &need, &empty);
+  if (vs != KGE_OK || empty) return vs;
+  if (!d->ids_out || !d->scores_out || !d->workspace) return fail(KGE_EINVAL, "kge_topk: null ids_out / scores_out / workspace");
+  if (d->workspace_bytes < need)
+    return fail(KGE_ENOMEM_WORKSPACE, "kge_topk: workspace %llu B < %llu B", (unsigned long long)d->workspace_bytes,
+                (unsigned long long)need);
+  const int sk = d->q.score_kind == KGE_SCORE_DOT ? SK_DOT : score_sk(d->q.score_kind, d->q.score_p);
+  const kge_status ls = launch_topk(A, T, P, d->q.mode, d->q.proj, sk, (hipStream_t)stream);
+  if (ls == KGE_EHIP)
+    return fail(KGE_EHIP, "kge_topk: clearing the filter bitmap: %s", hipGetErrorString(hipGetLastError()));
+  if (ls != KGE_OK)
+    return fail(KGE_EUNSUPPORTED, "no ranking instance for mode %d / score %d", d->q.mode, d->q.score_kind);
+  return hip_check("kge_topk");
 }
 
 kge_status kge_constrain_rows(kge_table t, int32_t kind, float value, void* stream) {

@@ -35,128 +35,9 @@
 // h * r; RESCAL R^T h / R t; RotatE h o w / w, t.
 #include <algorithm>
 
-#include "kge_step.h"
+#include "kge_rank_impl.h"
 
 namespace kge {
-
-// Scores of candidate entity `e` against NQ queries whose rows sit at
-// q0 + j * qs, q1 + j * qs, w + j * qs (any address space). The candidate's
-// elements are loaded once and used by every query; each query's sum runs in
-// the same element order for any NQ, so NQ = 1 (pos / filter passes) and
-// NQ = 8 (count pass) give identical bits. MODE: KGE_RANK_*; PJ: KGE_RPROJ_*.
-template <int MODE, int PJ, int SK, int NQ>
-__device__ __forceinline__ void rank_scores(const RankArgs& A, int64_t e, const float* q0, const float* q1,
-                                            const float* w, int qs, float (&out)[NQ]) {
-#pragma clang fp contract(off)
-  const float* x = A.cand + e * A.cand_ld;
-  const int D = A.dim;
-  float acc[NQ];
-#pragma unroll
-  for (int j = 0; j < NQ; ++j) acc[j] = 0.f;
-  auto lp = [&](float& ac, float a) {
-    const float m = fabsf(a);
-    if (SK == SK_P2) ac = ac + m * m;
-    else if (SK == SK_P1) ac = ac + m;
-    else if (SK == SK_PGEN) ac = ac + powf(m, A.p);
-    else ac = fmaxf(ac, m);
-  };
-  if (MODE == KGE_RANK_ROT) {
-    // complex pairs; t-side a = q0 - e, h-side a = e o q0 - q1
-    for (int c = 0; c < D; c += 2) {
-      const float er = x[c], ei = x[c + 1];
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) {
-        const float* a0 = q0 + j * qs;
-        float ar, ai;
-        if (A.hside) {
-          const float* a1 = q1 + j * qs;
-          const float xr = er * a0[c] - ei * a0[c + 1];
-          const float xi = er * a0[c + 1] + ei * a0[c];
-          ar = xr - a1[c];
-          ai = xi - a1[c + 1];
-        } else {
-          ar = a0[c] - er;
-          ai = a0[c + 1] - ei;
-        }
-        if (SK == SK_P2) acc[j] = acc[j] + (ar * ar + ai * ai);
-        else {
-          const float m = sqrtf(ar * ar + ai * ai);
-          acc[j] = SK == SK_P1 ? acc[j] + m : SK == SK_PGEN ? acc[j] + powf(m, A.p) : fmaxf(acc[j], m);
-        }
-      }
-    }
-  } else if (MODE == KGE_RANK_MUL || MODE == KGE_RANK_DOT) {
-    // DistMult sum(h * r * t): t-side q0 = h * r, h-side (e * r) * t;
-    // RESCAL: q0 = R^T h (t-side) or R t (h-side)
-    for (int c = 0; c < D; ++c) {
-      const float xe = x[c];
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) {
-        const float* a0 = q0 + j * qs;
-        acc[j] = acc[j] + ((MODE == KGE_RANK_MUL && A.hside) ? (xe * a0[c]) * q1[j * qs + c] : a0[c] * xe);
-      }
-    }
-  } else {
-    // translating: P(e) then t-side a = q0 - P(e), h-side a = (P(e) + q0) - q1
-    float dt[NQ], sc[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) { dt[j] = 0.f; sc[j] = 1.f; }
-    if (PJ == KGE_RPROJ_HYPER) {
-      for (int c = 0; c < D; ++c) {
-        const float xe = x[c];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) dt[j] = dt[j] + w[j * qs + c] * xe;
-      }
-    } else if (PJ == KGE_RPROJ_RANK1) {
-      // e_p . e is the candidate's own; the clip norm depends on the query's r_p
-      const float* ep = A.caux + e * A.caux_ld;
-      float de = 0.f;
-      for (int c = 0; c < A.ecols; ++c) de = de + ep[c] * x[c];
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) dt[j] = de;
-      if (A.clip) {
-        float n2[NQ];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) n2[j] = 0.f;
-        for (int c = 0; c < D; ++c) {
-          const float xe = c < A.kmin ? x[c] : 0.f;
-#pragma unroll
-          for (int j = 0; j < NQ; ++j) {
-            const float p = w[j * qs + c] * de + xe;
-            n2[j] = n2[j] + p * p;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-          const float n = sqrtf(n2[j]);
-          if (!(n < 1.f)) sc[j] = fmaxf(n, 1e-9f);
-        }
-      }
-    }
-    for (int c = 0; c < D; ++c) {
-      const float xe = (PJ != KGE_RPROJ_RANK1 || c < A.kmin) ? x[c] : 0.f;
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) {
-        const float* a0 = q0 + j * qs;
-        float p;
-        if (PJ == KGE_RPROJ_HYPER) p = xe - dt[j] * w[j * qs + c];
-        else if (PJ == KGE_RPROJ_RANK1) p = (w[j * qs + c] * dt[j] + xe) / sc[j];
-        else p = xe;
-        if (SK == SK_DOT) acc[j] = acc[j] + (A.hside ? (p + a0[c]) * q1[j * qs + c] : a0[c] * p);
-        else lp(acc[j], A.hside ? (p + a0[c]) - q1[j * qs + c] : a0[c] - p);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NQ; ++j) {
-    if (SK == SK_DOT || MODE == KGE_RANK_MUL || MODE == KGE_RANK_DOT) {
-      out[j] = acc[j];
-    } else {
-      float lpv;
-      out[j] = score_value<SK>(acc[j], A.pw, &lpv, A.p);
-    }
-  }
-}
 
 __device__ __forceinline__ const float* qrow(const float* base, const RankArgs& A, int64_t q) {
   return base ? base + q * A.ldq : nullptr;
@@ -215,14 +96,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_count_kernel(RankArgs A, in
   float* s0 = qs;
   float* s1 = qs + kRankQ * LQ;
   float* sw = qs + 2 * kRankQ * LQ;
-  // the group's query rows (rows past the set: zeros, results discarded)
-  for (int t = threadIdx.x; t < kRankQ * A.dim; t += kRankThreads) {
-    const int q = t / A.dim, c = t % A.dim;
-    const bool v = q < nq;
-    s0[q * LQ + c] = v ? A.q0[(q0i + q) * A.ldq + c] : 0.f;
-    s1[q * LQ + c] = (v && A.q1) ? A.q1[(q0i + q) * A.ldq + c] : 0.f;
-    sw[q * LQ + c] = (v && A.qw) ? A.qw[(q0i + q) * A.ldq + c] : 0.f;
-  }
+  rank_stage_queries<kRankQ>(A, q0i, nq, qs);
   float pos[kRankQ];
 #pragma unroll
   for (int q = 0; q < kRankQ; ++q) pos[q] = q < nq ? A.pos[q0i + q] : INFINITY;
@@ -265,106 +139,17 @@ __global__ __launch_bounds__(256) void rank_filter_kernel(RankArgs A) {
   if (lane_id() == 0) A.rank[q] = A.rank[q] - sub + 1ull;
 }
 
-// Register-tiled count pass for the element-wise scores (translating without
-// a projection: TransE, TransR's pre-projected candidates; DistMult; RESCAL):
-// a workgroup scores a 64-query x 64-candidate tile, each thread 4 x 4 pairs
-// held in registers, over 16-element chunks staged transposed in LDS
-// ([element][row]: a thread's four queries and four candidates are one
-// ds_read_b128 each). Candidate rows are read once per 64 queries and with
-// whole-row float4 loads (the lane-per-candidate pass reads 4 bytes of 64
-// different rows per instruction). Every pair's sum runs over the elements in
-// ascending order with the same ops as rank_scores, so the scores -- and the
-// strict > comparisons -- are bit for bit those of the pos / filter passes.
-constexpr int kRT = 64;    // queries / candidates per tile
-constexpr int kRC = 16;    // elements per staged chunk
-
+// Register-tiled count pass for the element-wise scores (rank_tile_scores,
+// kge_rank_impl.h): a workgroup scores a 64-query x 64-candidate tile and
+// counts, per query, the unfiltered candidates strictly above its true score.
 template <int MODE, int SK, bool HS>
 __global__ __launch_bounds__(256) void rank_tile_kernel(RankArgs A, int64_t qt0) {
-#pragma clang fp contract(off)
-  using f2 = __attribute__((ext_vector_type(2))) float;
-  __shared__ __attribute__((aligned(16))) float sq0[kRC][kRT];
-  __shared__ __attribute__((aligned(16))) float sq1[kRC][kRT];
-  __shared__ __attribute__((aligned(16))) float sx[kRC][kRT];
   const int tid = threadIdx.x, tq = tid >> 4, tc = tid & 15;
   const int64_t c0 = (int64_t)blockIdx.x * kRT, q0i = (qt0 + blockIdx.y) * kRT;
-  constexpr bool two = (MODE == KGE_RANK_TRANS || MODE == KGE_RANK_MUL) && HS;   // h-side: q1 too
-  const int D = A.dim;
-  // pairs (i, 2jp) and (i, 2jp + 1) side by side: the element ops run as
-  // packed f32 (v_pk_add / v_pk_mul), each lane of a pair in the scalar order
-  f2 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = f2{0.f, 0.f};
-  // staging: thread t loads row (t >> 2) elements 4 (t & 3) .. +3 of each tile
-  const int sr = tid >> 2, se = (tid & 3) * 4;
-  const int64_t qr = q0i + sr, er = c0 + sr;
-  const bool qv = qr < A.n, ev = er < A.E;
-  // bitmap filter: the word holding this thread's four candidates, per query
-  // (c0 is a multiple of 64, so 4 tc .. 4 tc + 3 share one word)
-  uint32_t fmask[4] = {0u, 0u, 0u, 0u};
-  if (A.fbits && c0 + 4 * tc < A.E) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t q = q0i + 4 * tq + i;
-      if (q < A.n) fmask[i] = A.fbits[q * A.fw + ((c0 + 4 * tc) >> 5)] >> (uint32_t)((4 * tc) & 31);
-    }
-  }
-  for (int e0 = 0; e0 < D; e0 += kRC) {
-    const int ne = min(kRC, D - e0);
-    float a[4], b[4], x[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = e0 + se + u;
-      const bool in = se + u < ne;
-      a[u] = (qv && in) ? A.q0[qr * A.ldq + c] : 0.f;
-      b[u] = (two && qv && in) ? A.q1[qr * A.ldq + c] : 0.f;
-      x[u] = (ev && in) ? A.cand[er * A.cand_ld + c] : 0.f;
-    }
-    __syncthreads();   // the previous chunk is consumed
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      sq0[se + u][sr] = a[u];
-      if (two) sq1[se + u][sr] = b[u];
-      sx[se + u][sr] = x[u];
-    }
-    __syncthreads();
-    for (int c = 0; c < ne; ++c) {
-      const float4 qa = *reinterpret_cast<const float4*>(&sq0[c][4 * tq]);
-      const float4 xa = *reinterpret_cast<const float4*>(&sx[c][4 * tc]);
-      float4 qb = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (two) qb = *reinterpret_cast<const float4*>(&sq1[c][4 * tq]);
-      const float qv0[4] = {qa.x, qa.y, qa.z, qa.w}, qv1[4] = {qb.x, qb.y, qb.z, qb.w};
-      const f2 xp[2] = {f2{xa.x, xa.y}, f2{xa.z, xa.w}};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f2 a0 = f2{qv0[i], qv0[i]}, a1 = f2{qv1[i], qv1[i]};
-#pragma unroll
-        for (int jp = 0; jp < 2; ++jp) {
-          const f2 xe = xp[jp];
-          f2& ac = acc[i][jp];
-          if (MODE == KGE_RANK_MUL) {
-            ac = ac + (HS ? (xe * a0) * a1 : a0 * xe);
-          } else if (MODE == KGE_RANK_DOT) {
-            ac = ac + a0 * xe;
-          } else if (SK == SK_DOT) {
-            ac = ac + (HS ? (xe + a0) * a1 : a0 * xe);
-          } else {
-            const f2 d = HS ? (xe + a0) - a1 : a0 - xe;
-            if (SK == SK_P2) {
-              ac = ac + d * d;   // |d| |d| == d d bit for bit
-            } else {
-#pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                const float m = fabsf(d[h]);
-                if (SK == SK_P1) ac[h] = ac[h] + m;
-                else if (SK == SK_PGEN) ac[h] = ac[h] + powf(m, A.p);
-                else ac[h] = fmaxf(ac[h], m);
-              }
-            }
-          }
-        }
-      }
-    }
-  }
+  uint32_t fmask[4];
+  rank_tile_fmask(A, q0i, c0, fmask);
+  float sc[4][4];
+  rank_tile_scores<MODE, SK, HS>(A, q0i, c0, sc);
   // strict > the query's true score; counts summed over the 16 lanes of a row
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -372,17 +157,8 @@ __global__ __launch_bounds__(256) void rank_tile_kernel(RankArgs A, int64_t qt0)
     const float pv = q < A.n ? A.pos[q] : INFINITY;
     unsigned cnt = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float av = acc[i][j >> 1][j & 1];
-      float sc;
-      if (SK == SK_DOT || MODE == KGE_RANK_MUL || MODE == KGE_RANK_DOT) {
-        sc = av;
-      } else {
-        float lpv;
-        sc = score_value<SK>(av, A.pw, &lpv, A.p);
-      }
-      cnt += (c0 + 4 * tc + j < A.E && sc > pv && !((fmask[i] >> j) & 1u)) ? 1u : 0u;
-    }
+    for (int j = 0; j < 4; ++j)
+      cnt += (c0 + 4 * tc + j < A.E && sc[i][j] > pv && !((fmask[i] >> j) & 1u)) ? 1u : 0u;
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) cnt += (unsigned)__shfl_xor((int)cnt, o, KGE_WAVE);
     if (tc == 0 && q < A.n && cnt) atomicAdd(&A.rank[q], (unsigned long long)cnt);
@@ -511,17 +287,20 @@ static void rank_by_sk(const RankArgs& A, int sk, hipStream_t st) {
   }
 }
 
-kge_status launch_rank(const RankArgs& A, int mode, int proj, int sk, hipStream_t st) {
-  if (A.fbits) {   // the filter bitmap, before the passes that read it
-    uint32_t* bits = const_cast<uint32_t*>(A.fbits);
-    if (A.fw <= kBitsLds) {
-      hipLaunchKernelGGL(rank_bits_kernel<true>, dim3((unsigned)A.n), dim3(256), 0, st, A, bits);
-    } else {
-      // a failed clear would leave the caller's stale words as filter bits
-      if (hipMemsetAsync(bits, 0, (size_t)(A.n * A.fw) * sizeof(uint32_t), st) != hipSuccess) return KGE_EHIP;
-      hipLaunchKernelGGL(rank_bits_kernel<false>, dim3((unsigned)A.n), dim3(256), 0, st, A, bits);
-    }
+kge_status launch_rank_bits(const RankArgs& A, hipStream_t st) {
+  uint32_t* bits = const_cast<uint32_t*>(A.fbits);
+  if (A.fw <= kBitsLds) {
+    hipLaunchKernelGGL(rank_bits_kernel<true>, dim3((unsigned)A.n), dim3(256), 0, st, A, bits);
+  } else {
+    // a failed clear would leave the caller's stale words as filter bits
+    if (hipMemsetAsync(bits, 0, (size_t)(A.n * A.fw) * sizeof(uint32_t), st) != hipSuccess) return KGE_EHIP;
+    hipLaunchKernelGGL(rank_bits_kernel<false>, dim3((unsigned)A.n), dim3(256), 0, st, A, bits);
   }
+  return KGE_OK;
+}
+
+kge_status launch_rank(const RankArgs& A, int mode, int proj, int sk, hipStream_t st) {
+  if (A.fbits && launch_rank_bits(A, st) != KGE_OK) return KGE_EHIP;   // before the passes that read it
   switch (mode) {
     case KGE_RANK_TRANS:
       if (proj == KGE_RPROJ_HYPER) rank_by_sk<KGE_RANK_TRANS, KGE_RPROJ_HYPER>(A, sk, st);

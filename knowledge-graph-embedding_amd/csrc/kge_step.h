@@ -433,6 +433,30 @@ struct RankArgs {
 };
 
 kge_status launch_rank(const RankArgs& A, int mode, int proj, int sk, hipStream_t st);
+// The filter bitmap A.fbits from A.fbeg / fend / fent (KGE_EHIP: the clear failed).
+kge_status launch_rank_bits(const RankArgs& A, hipStream_t st);
+
+// ---- top-k link prediction (kge_topk.hip)
+// How a call is laid out: the producer, its queries per workgroup, the keys
+// per query buffer, and the candidate slabs -- a function of the descriptor
+// alone, so kge_topk_workspace_bytes and kge_topk agree.
+struct TopkPlan {
+  bool tiled;          // register-tiled producer (64 queries / workgroup)
+  int32_t nq;          // lane producer: queries per workgroup (8 or 2)
+  int32_t cap;         // keys per query buffer in LDS: a power of two >= 2 k
+  int64_t slab;        // candidates per slab (a multiple of 256)
+  int64_t nslab;
+  uint32_t lds_bytes;  // lane producer: dynamic LDS
+};
+struct TopkArgs {
+  int32_t k;
+  bool out64;                  // ids_out is int64
+  void* ids; float* scores; int32_t* count;
+  unsigned long long* lists;   // workspace: [n, nslab, k] keys, best first, 0 = none
+};
+TopkPlan topk_plan(int mode, int proj, int dim, int64_t n, int64_t E, int k, int flags);
+kge_status launch_topk(const RankArgs& A, const TopkArgs& T, const TopkPlan& P, int mode, int proj, int sk,
+                       hipStream_t st);
 void launch_stream(const void* tri, bool i64, int64_t n, int64_t start, int64_t batch, uint64_t seed, int shuffle,
                    void* out, hipStream_t st);
 void launch_stream_perm(int64_t n, uint64_t seed, int64_t epoch, int32_t* perm, hipStream_t st);
