@@ -85,6 +85,12 @@ kge_status make_plan(const kge_step_desc* d, Plan* pl) {
   if (d->dim <= 0) return fail(KGE_EINVAL, "dim must be > 0");
   const bool rescal = model == KGE_MODEL_RESCAL, transr = model == KGE_MODEL_TRANSR;
   const bool td = model == KGE_MODEL_TRANSD, proj = td || model == KGE_MODEL_TRANSH;
+#ifdef KGE_ONLY_ONE
+  // tuning builds (tools/variants.py): this unit's plan follows the build's
+  // knobs, the other families' objects the defaults -- they are not launched
+  if (rescal || transr || proj || (d->flags & (KGE_FLAG_OWNER | KGE_FLAG_OWNER_MERGE)))
+    return fail(KGE_EUNSUPPORTED, "tuning build (KGE_ONLY_ONE): element-wise training steps only");
+#endif
   const int64_t entc = model == KGE_MODEL_ROTATE ? 2 * (int64_t)d->dim : d->dim;
   // RESCAL: [R, d, d] matrices; TransR: rel_emb [R, k] (+ rel_proj [R, d, k] in rel_aux);
   // TransD: rel_emb / rel_proj [R, k]
@@ -223,9 +229,10 @@ kge_status make_plan(const kge_step_desc* d, Plan* pl) {
     const int Keff_ = d->corrupt_side == KGE_SIDE_HT ? 2 * (d->negative_ratio / 2) : d->negative_ratio;
     if (Keff_ + 1 > kTrMaxSlots)
       return fail(KGE_EUNSUPPORTED, "TransR fused step supports negative_ratio <= %d", kTrMaxSlots - 1);
-    const TrLds TL = tr_lds(d->dim, d->dim_rel, Keff_);
-    if ((size_t)TL.total_floats * 4 + 256 > 160 * 1024)
-      return fail(KGE_EUNSUPPORTED, "TransR LDS budget exceeded (%d bytes)", TL.total_floats * 4);
+    // (inherited from the retired one-per-CU kernel's LDS carve; transr2_kernel's own would admit more)
+    if (std::max(d->dim, d->dim_rel) > kTrBigDim && Keff_ > kTrBigDimMaxNeg)
+      return fail(KGE_EUNSUPPORTED, "TransR fused step supports negative_ratio <= %d for embedding sizes above %d",
+                  kTrBigDimMaxNeg, kTrBigDim);
   }
   const int nc = (int)ceil_div(rowlen, 64 * vec);
   if (nc > 4)
@@ -1018,6 +1025,9 @@ kge_status kge_sample(const kge_sample_desc* d, void* stream) {
 // 0). *empty: n == 0, nothing to do.
 static kge_status rank_args(const kge_rank_desc* d, bool topk, RankArgs& A, bool* empty) {
   *empty = false;
+#ifdef KGE_ONLY_ONE
+  return fail(KGE_EUNSUPPORTED, "tuning build (KGE_ONLY_ONE): no %s", topk ? "kge_topk" : "kge_rank");
+#endif
   if (d->abi_version != KGE_ABI_VERSION)
     return fail(KGE_EINVAL, "abi_version %d != library %d", d->abi_version, KGE_ABI_VERSION);
   if (d->mode < KGE_RANK_TRANS || d->mode > KGE_RANK_DOT) return fail(KGE_EINVAL, "unknown rank mode %d", d->mode);

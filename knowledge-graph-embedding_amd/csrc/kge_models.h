@@ -414,7 +414,7 @@ struct DistMult {
     load_ctx_raw(c, ent, rel, h, r, t);
     ctx_finish(c, mp);
   }
-  // the two halves (the score kernel's KGE_CTX_LATE): raw rows, then the
+  // the two halves (the score kernel's late context): raw rows, then the
   // normalisation and the products
   __device__ static void load_ctx_raw(Ctx& c, const TabView& ent, const TabView& rel, int64_t h, int64_t r,
                                       int64_t t) {
@@ -512,7 +512,7 @@ struct RotatE {
     load_ctx_raw(c, ent, rel, h, r, t);
     ctx_finish(c, mp);
   }
-  // the two halves (the score kernel's KGE_CTX_LATE): the raw rows (the
+  // the two halves (the score kernel's late context): the raw rows (the
   // phases parked in CS's first half), then (cos, sin) and X = H o w
   __device__ static void load_ctx_raw(Ctx& c, const TabView& ent, const TabView& rel, int64_t h, int64_t r,
                                       int64_t t) {

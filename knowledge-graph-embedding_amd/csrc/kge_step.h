@@ -348,7 +348,8 @@ __device__ __forceinline__ int64_t rel_lower(const int32_t* srel, int64_t lo, in
   return lo;
 }
 
-// ---- TransR (kge_transr.hip): one workgroup per positive, three MFMA products
+// ---- TransR: one workgroup per positive, three MFMA products (transr2_kernel,
+// kge_transr2.h); launches, materialised update and rel_proj apply in kge_transr.hip
 struct TrArgs {
   TabView proj;      // rel_proj [R, d * k] (M_r row-major [d][k])
   int32_t d, k;      // entity / relation embedding sizes
@@ -361,47 +362,18 @@ struct TrArgs {
 };
 constexpr int kTrWaves = 8;
 constexpr int kTrThreads = kTrWaves * KGE_WAVE;
-constexpr int kTrMaxSlots = 72;   // K + 1 slots over 8 waves, 9 per wave in registers
+constexpr int kTrMaxSlots = 72;   // K + 1 slots: at most five 16-row tiles of negatives
 constexpr int kTrMaxDim = 256;    // d, k (MFMA k-steps held in registers)
+// the plan's TransR gate (kge_abi.hip): max(d, k) above kTrBigDim (16 column
+// chunks, tr_nc below) takes at most kTrBigDimMaxNeg effective negatives
+constexpr int kTrBigDim = 208;
+constexpr int kTrBigDimMaxNeg = 62;
 // GEMM1 / GEMM2 inner dimensions run over NC whole 16-column chunks, a
 // compile-time count (straight-line MFMA code, B columns in 4*NC registers):
 // the smallest of 4, 8, 13, 16 covering max(d, k)
 __host__ __device__ inline int tr_nc(int d, int k) {
   const int c = ((d > k ? d : k) + 15) / 16;
   return c <= 4 ? 4 : c <= 8 ? 8 : c <= 13 ? 13 : 16;
-}
-// LDS carve of the TransR kernel (floats): X [NR16][LX] | P [NR16][LP], later
-// S [SR16][LP] over both; then per-row / per-slot scalars and partials.
-// Rows are W = 16 NC floats (zero past d / k) plus 4: the stride mod 32 banks
-// is 4 or 20, so the 8 rows served together by a ds_read_b128 operand fetch
-// hit disjoint bank quads.
-struct TrLds {
-  int NC, W, LX, LP, NR16, SR16;
-  int pn, xx, xh, xt, sS, sR, sT, sA, rp, ids, misc, total_floats;
-};
-__host__ __device__ inline TrLds tr_lds(int d, int k, int K) {
-  TrLds L;
-  L.NC = tr_nc(d, k);
-  L.W = 16 * L.NC;
-  L.LX = L.W + 4;
-  L.LP = L.W + 4;
-  L.NR16 = (K + 2 + 15) & ~15;
-  L.SR16 = (2 * K + 4 + 15) & ~15;
-  int o = L.NR16 * (L.LX + L.LP);
-  if (L.SR16 * L.LP > o) o = L.SR16 * L.LP;
-  L.pn = o; o += L.NR16;
-  L.xx = o; o += L.NR16;
-  L.xh = o; o += L.NR16;
-  L.xt = o; o += L.NR16;
-  L.sS = o; o += (K + 4) & ~3;
-  L.sR = o; o += (K + 4) & ~3;
-  L.sT = o; o += (K + 4) & ~3;
-  L.sA = o; o += (K + 4) & ~3;
-  L.rp = o; o += kTrWaves * L.LP;
-  L.ids = o; o += (K + 3) & ~3;
-  L.misc = o; o += 64;
-  L.total_floats = o;
-  return L;
 }
 kge_status launch_step_transr(const StepArgs& A, const StepGeom& G, const TrArgs& T, const RelArgs& P, int sk,
                               hipStream_t st, hipEvent_t const* ev);

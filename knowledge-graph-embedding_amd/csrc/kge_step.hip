@@ -495,7 +495,8 @@ void launch_merge_segsum(const StepArgs& A, hipStream_t st) {
 kge_status launch_step_elementwise(const StepArgs& A, const StepGeom& G, int model, int sk,
                                    hipStream_t st, hipEvent_t const* ev) {
 #ifdef KGE_ONLY_ONE
-  // quick-iteration builds (tools/phase_prof.py): the bench's C2 instance only
+  // tuning builds (tools/variants.py, tools/phase_prof.py): the bench's C2
+  // instance only, compiled with the build's knobs
   if (model == KGE_MODEL_TRANSE && G.vec == 4 && G.nc == 1 && sk == SK_P2 && A.side_mode == KGE_SIDE_HT)
     return launch_family<TransE, 4, 1, SK_P2>(A, G, st, ev);
   return KGE_EUNSUPPORTED;
@@ -508,19 +509,6 @@ kge_status launch_step_elementwise(const StepArgs& A, const StepGeom& G, int mod
   }
 #endif
 }
-
-#ifdef KGE_ONLY_ONE
-// single-instance builds (tools/phase_prof.py, tools/variants.py): the other families are stubs
-kge_status launch_step_proj(const StepArgs&, const StepGeom&, const PjPlan&, int, hipStream_t, hipEvent_t const*) {
-  return KGE_EUNSUPPORTED;
-}
-kge_status launch_rank(const RankArgs&, int, int, int, hipStream_t) { return KGE_EUNSUPPORTED; }
-kge_status launch_step_rescal(const StepArgs&, const StepGeom&, const RelArgs&, float, float*, hipStream_t,
-                              hipEvent_t const*) {
-  return KGE_EUNSUPPORTED;
-}
-#endif
-
 
 }  // namespace kge
 

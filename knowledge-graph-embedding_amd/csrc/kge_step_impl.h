@@ -33,9 +33,6 @@
 
 #include "kge_step.h"
 
-#ifndef KGE_SCORE_PREFETCH
-#define KGE_SCORE_PREFETCH 0   // score kernel: software-pipelined row batches (tuning knob)
-#endif
 #ifndef KGE_STREAM_ROWS
 #define KGE_STREAM_ROWS 8   // sampled rows per stream batch at NC = 1 (tuning knob)
 #endif
@@ -48,25 +45,6 @@
 #ifndef KGE_UPD_WIDE_WPE
 #define KGE_UPD_WIDE_WPE 1      // update launches of wide rows (NC >= 2 or WIDE): amdgpu_waves_per_eu (tuning knob)
 #endif
-#ifndef KGE_COMPACT_LIST0
-#define KGE_COMPACT_LIST0 1 // compact launches: list position 0 lives only in the leader table (A-B knob)
-#endif
-#ifndef KGE_GUARD_KU
-#define KGE_GUARD_KU 1      // update kernel: workspace plan guard at entry (tuning / A-B knob)
-#endif
-#ifndef KGE_FILE_EARLY
-// score kernel: when the negatives' keys are filed. 2 (default): each lane's
-// slot claims its destination (counter add / hash-slot CAS) right after the
-// row stream and stores the code after the merge barrier, so the claim's
-// round trip hides under the barrier wait and the merge (C2 KS 53.7 -> 48.7
-// us, profiles/r06e); 1: claims after the first batch's loads (slower: 55.4);
-// 0: claim and store in the finalise pass (A-B knob)
-#define KGE_FILE_EARLY 2
-#endif
-#ifndef KGE_CTX_LATE
-#define KGE_CTX_LATE 1      // score kernel: the positive's context rows finished after the first row batch's
-                            // loads are issued (one dependent round trip fewer per wave) (A-B knob)
-#endif
 #ifndef KGE_UPDATE_U
 #define KGE_UPDATE_U 8      // update kernel: list entries in flight per wave at NC = 1 (tuning knob)
 #endif
@@ -75,7 +53,7 @@ namespace kge {
 
 #ifdef KGE_PHASE_PROF
 // one counter array per translation unit (no relocatable device code): each
-// profiled TU exports its own reader (kge_prof_read, kge_trprof_read)
+// profiled TU exports its own reader (kge_prof_read, kge_trprof2_read)
 static __device__ unsigned long long g_kge_prof[64];
 #endif
 
@@ -207,7 +185,7 @@ __device__ __forceinline__ void bin_commit(const StepArgs& A, int64_t dest, uint
     A.leaders[kpos] = make_uint4((uint32_t)dest, c.r == 0u ? code : 0xFFFFFFFFu, c.h, 0u);
     // position 0's code is the leader table's (a 50M-row table's destinations
     // mostly hold one key: no scattered list store for them at all)
-    if (KGE_COMPACT_LIST0 && c.r == 0u) return;
+    if (c.r == 0u) return;
   }
   if (c.r < (uint32_t)A.cap) {
     A.list[li * A.cap + c.r] = code;
@@ -488,11 +466,15 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
   }
   KGE_PROF(0);
 
-  // early filing (KGE_FILE_EARLY): this lane's slot jbeg + lane, its claim
+  // early filing: this lane's slot jbeg + lane claims its destination (counter
+  // add / hash-slot CAS) right after the row stream and stores the code after
+  // the merge barrier, so the claim's round trip hides under the barrier wait
+  // and the merge (C2 KS 53.7 -> 48.7 us, profiles/r06e; claiming after the
+  // first batch was slower, 55.4 us)
   // (not for the wide instances -- rows of two chunks, RotatE, DistMult: their
   // 2-waves-per-SIMD budget is nearly full and the claims' registers spilled)
   constexpr bool NARROW = !(NC >= 2 || M::WIDE);
-  const bool early = KGE_FILE_EARLY != 0 && NARROW && !OWN && A.train && A.SW <= KGE_WAVE;
+  const bool early = NARROW && !OWN && A.train && A.SW <= KGE_WAVE;
   const int jfile = jbeg + lane;
   int64_t kdest = 0;
   KeyClaim kc{0u, 0u};
@@ -555,9 +537,10 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
     }
     __syncthreads();   // `red` is reused for the wave states below
   }
-  // KGE_CTX_LATE: the context rows' loads go out now, their combination (and
-  // the positive's score) after the first row batch's loads are issued
-  constexpr bool LATE = KGE_CTX_LATE && NARROW && !OWN && ctx_split<M>::v;   // (wide instances: it spilled, C3)
+  // late context: the context rows' loads go out now, their combination (and
+  // the positive's score) after the first row batch's loads are issued (one
+  // dependent round trip fewer per wave)
+  constexpr bool LATE = NARROW && !OWN && ctx_split<M>::v;   // (wide instances: it spilled, C3)
   bool ctx_done = !LATE;
   if constexpr (!M::SELF_CTX) {
     if (active) {
@@ -603,8 +586,8 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
         else load_row(dst[u], row, A.ent.cols);
       }
     };
-    // KGE_SCORE_PREFETCH: the next batch's rows are in flight while this
-    // batch is reduced and differentiated (one more batch of registers)
+    // (no software pipelining of the row batches: a second batch of
+    // registers in flight measured slower or unchanged, round 2)
     // one range [sb, se) of slots whose corruption kinds follow the
     // pattern S2 (the launch's side; the owner pass: one side per range).
     // LK: the loss kind when known at compile time (SANS, the configs' loss:
@@ -613,21 +596,10 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
     constexpr int S2 = decltype(sidec)::value;
     constexpr int LK = decltype(lkc)::value;
     const int lk = LK >= 0 ? LK : A.loss_kind;
-    F En[KGE_SCORE_PREFETCH ? ROWS : 1];
-    if constexpr (KGE_SCORE_PREFETCH) issue(En, sb, sb, se);
     for (int j0 = sb; j0 < se; j0 += ROWS) {
       const int nrow = min(ROWS, se - j0);   // wave-uniform, >= 1
       F E[ROWS];
-      if constexpr (KGE_SCORE_PREFETCH) {
-#pragma unroll
-        for (int u = 0; u < ROWS; ++u) E[u] = En[u];
-        if (j0 + ROWS < se) issue(En, j0 + ROWS, sb, se);
-      } else {
-        issue(E, j0, sb, se);
-      }
-      if constexpr (KGE_FILE_EARLY == 1 && !OWN) {
-        if (early && j0 == sb) claim_early();
-      }
+      issue(E, j0, sb, se);
       if constexpr (LATE) {
         if (!ctx_done) pos_score();
       }
@@ -722,9 +694,6 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
         const float Mu = SK == SK_PINF ? bcast(Rl, u << SH) : SK == SK_PGEN ? A.p : 0.f;
         M::template bwdk<kind_at<S2>(u)>(ctx, E[u], a[u], b[u], alu, Mu, accH, accR, accT, nrm, mp);
       });
-      if constexpr (KGE_FILE_EARLY == 1 && !OWN) {
-        if (early && j0 == sb) commit_early();
-      }
     }
     };
     auto stream_lk = [&](auto sidec, const int sb, const int se) {
@@ -734,29 +703,25 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
     if constexpr (OWN) {
       stream_lk(std::integral_constant<int, SIDE == KGE_SIDE_HT ? KGE_SIDE_H : SIDE>{}, hb, he);
       if constexpr (SIDE == KGE_SIDE_HT) stream_lk(std::integral_constant<int, KGE_SIDE_T>{}, tb, te);
-      if constexpr (KGE_FILE_EARLY == 2) {
-        // the owned slots' claims (lane l: slot hb + l, slot tb + l), stored
-        // by the finalise pass after the merge
-        const uint32_t kb = __builtin_bit_cast(uint32_t, s_mrg[grp * MG_STRIDE + MG_KB]);
-        early_own = A.train && he - hb <= KGE_WAVE && te - tb <= KGE_WAVE;
-        if (early_own) {
-          __builtin_amdgcn_sched_barrier(0);
+      // the owned slots' claims (lane l: slot hb + l, slot tb + l), stored
+      // by the finalise pass after the merge
+      const uint32_t kb = __builtin_bit_cast(uint32_t, s_mrg[grp * MG_STRIDE + MG_KB]);
+      early_own = A.train && he - hb <= KGE_WAVE && te - tb <= KGE_WAVE;
+      if (early_own) {
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int r = 0; r < 2; ++r) {
-            const int c = (r ? tb : hb) + lane;
-            if (c < (r ? te : he) && kb + (uint32_t)c < A.own_cap) kco[r] = bin_claim(A, ids[c]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
+        for (int r = 0; r < 2; ++r) {
+          const int c = (r ? tb : hb) + lane;
+          if (c < (r ? te : he) && kb + (uint32_t)c < A.own_cap) kco[r] = bin_claim(A, ids[c]);
         }
+        __builtin_amdgcn_sched_barrier(0);
       }
     } else {
       stream_lk(std::integral_constant<int, SIDE>{}, jbeg, jend);
       if constexpr (LATE) {
         if (!ctx_done) pos_score();   // (a wave with no slots)
       }
-      if constexpr (KGE_FILE_EARLY == 2) {
-        if (early) claim_early();
-      }
+      if (early) claim_early();
     }
     M::finish(accH, accR, accT);
   }
@@ -828,7 +793,7 @@ __global__ __launch_bounds__(kStepThreads) __attribute__((amdgpu_waves_per_eu((N
   }
   __syncthreads();
   KGE_PROF(2);
-  if constexpr (KGE_FILE_EARLY == 2 && !OWN) {
+  if constexpr (!OWN) {
     if (active && early) commit_early();
   }
 
@@ -1221,7 +1186,7 @@ void update_kernel(StepArgs A) {
   // workspace for this plan or refused it (and reported); here a refused
   // workspace just leaves every wave idle -- one scalar compare, no branch
   // of its own (an early return cost the compact instance registers)
-  const bool ws_ok = !KGE_GUARD_KU || *reinterpret_cast<const uint32_t*>(&A.ctl->plan_sig) == A.sig;
+  const bool ws_ok = *reinterpret_cast<const uint32_t*>(&A.ctl->plan_sig) == A.sig;
   // split step, a rank's exchange failed: no table, gradient or relation
   // write at all, but every destination's counter / hash slot still goes
   // back to zero -- the workspace is ready for the next step's score pass
@@ -1341,7 +1306,7 @@ void update_kernel(StepArgs A) {
     }
     // list entry q (compact launches: position 0 is the leader's code1, and
     // the list is read only once the count says there is more than one key)
-    const bool l0 = KGE_COMPACT_LIST0 && CMP;
+    const bool l0 = CMP;
     auto lst_at = [&](uint32_t q) -> uint32_t { return (l0 && q == 0u) ? code1 : lst[q]; };
     uint32_t code0 = 0xFFFFFFFFu;
     if (!CMP) code0 = lst[min(lane, A.cap - 1)];   // speculative: issued with the counter
@@ -1738,7 +1703,7 @@ __global__ __launch_bounds__(1024) void long_rows_kernel(StepArgs A) {
     const uint32_t n = (uint32_t)A.htab[li];
     const uint32_t nl = min(n, (uint32_t)A.cap);
     const uint32_t* lst = A.list + li * (int64_t)A.cap;
-    for (uint32_t q = tid; q < nl; q += 1024) s_codes[q] = (KGE_COMPACT_LIST0 && q == 0u) ? w.w : lst[q];
+    for (uint32_t q = tid; q < nl; q += 1024) s_codes[q] = q == 0u ? w.w : lst[q];
     if (tid == 0) s_fill = nl;
     __syncthreads();
     if (n > nl) {
@@ -1900,7 +1865,7 @@ static inline void launch_rel_seg(const StepArgs& A, hipStream_t st) {
 // ------------------------------------------------------------ dispatch
 template <template <int, int, int> class Model, int VEC, int NC, int SK>
 static void launch_score(const StepArgs& A, const StepGeom& G, hipStream_t st) {
-#ifdef KGE_ONLY_ONE
+#ifdef KGE_ONLY_ONE   // (tuning builds of kge_step.hip: the bench's C2 instance only, 'h+t')
   hipLaunchKernelGGL((score_kernel<Model, VEC, NC, SK, KGE_SIDE_HT>), dim3(G.nWG), dim3(kStepThreads), G.lds_score,
                      st, A);
 #else
@@ -1940,7 +1905,6 @@ static kge_status launch_family(const StepArgs& A, const StepGeom& G, hipStream_
   return KGE_OK;
 }
 
-#ifndef KGE_ONLY_ONE
 template <template <int, int, int> class Model, int VEC, int NC>
 static kge_status by_sk(const StepArgs& A, const StepGeom& G, int sk, hipStream_t st, hipEvent_t const* ev) {
   switch (sk) {
@@ -1962,7 +1926,5 @@ static kge_status by_sk_lp(const StepArgs& A, const StepGeom& G, int sk, hipStre
     default: return KGE_EUNSUPPORTED;
   }
 }
-
-#endif  // KGE_ONLY_ONE
 
 }  // namespace kge

@@ -4,7 +4,6 @@
 
 namespace kge {
 
-#ifndef KGE_ONLY_ONE
 // RESCAL: relation rank -> score (its waves form u = R^T h, v = R t, stream
 // the negatives as dot products against them, then g_h = R A, g_t = R^T B)
 // -> regulariser loss -> dR pass -> update kernel (dense entity gradient)
@@ -56,7 +55,5 @@ kge_status launch_step_rescal(const StepArgs& A, const StepGeom& G, const RelArg
   if (G.nc == 2) return rescal_vn<1, 2>(A, G, P, lam, regpart, st, ev);
   return rescal_vn<1, 4>(A, G, P, lam, regpart, st, ev);
 }
-#endif  // KGE_ONLY_ONE
-
 
 }  // namespace kge

@@ -1,7 +1,8 @@
-// TransR step kernel, two positives per CU (transr2_kernel), and the fp32
-// MFMA helpers it shares with transr_kernel (kge_transr.hip). Instantiated
-// per score kind by kge_transr2_*.hip (launch_transr2<SK>), so the kinds
-// compile in parallel.
+// TransR step kernel, two positives per CU (transr2_kernel), with its fp32
+// MFMA helpers (v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][k = l >> 4],
+// B[k = l >> 4][l & 15], C[(l >> 4) * 4 + reg][l & 15]). Instantiated per
+// score kind by kge_transr2_*.hip (launch_transr2<SK>), so the kinds compile
+// in parallel; kge_transr.hip holds the host side and the update passes.
 #pragma once
 #include "kge_step_impl.h"
 
@@ -13,7 +14,6 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-constexpr int kTrQ = (kTrMaxSlots + kTrWaves - 1) / kTrWaves;   // slots per wave
 constexpr int kTrKV = kTrMaxDim / KGE_WAVE;                     // projected-row floats per lane
 constexpr int kTrKS3 = ((kTrMaxSlots + 1 + 15) / 16) * 4;       // GEMM3 k-steps (K + 2 slot rows, 16-padded)
 
@@ -73,9 +73,9 @@ __device__ __forceinline__ void mfma_one_b128(f32x4& a0, const float* p0, const 
 }
 
 // ============================================================ two positives per CU
-// The same three products in <= 128 VGPRs and ~78 KB of LDS, so two
-// workgroups share a CU and one's VALU phases run under the other's MFMA
-// (transr_kernel: 144 KB, 197 VGPRs -> one workgroup per CU).
+// The three products of a positive (kge_transr.hip's header) in <= 128 VGPRs
+// and ~78 KB of LDS, so two workgroups share a CU and one's VALU phases run
+// under the other's MFMA.
 //
 // P = X M_r never goes to LDS. Wave role w owns P's column tiles w and w + 8
 // over every row tile, in MFMA accumulator layout: lane l holds column

@@ -19,6 +19,8 @@ Fixtures and where their expected values come from:
                      plugin combination on the toy KG with seeded weights and
                      injected negatives: float64 oracle outputs (loss, scores,
                      updated tables, per-variable gradient norm^2).
+  transr_plan.json   has its own generator, make_transr_plan_golden.py (the
+                     step plan's answers for TransR descriptors; no oracle).
 The reference's own tests pin only properties, so the step
 vectors are the oracle's (PARITY UNPINNED against TF, which is absent);
 they freeze the restatement so that regressions in either side show up.

@@ -12,7 +12,6 @@ microseconds per workgroup per phase, i.e. where one workgroup's time goes.
 import argparse
 import ctypes
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,15 +28,11 @@ UPDATE_PHASES = {16: "dest rows (sort+sum+apply)"}
 
 
 def build(extra=()):
-    objs = []
-    for src in ("kge_step.hip", "kge_abi.hip", "kge_transr.hip", "kge_rel.hip", "kge_stream.hip", "kge_exchange.hip"):
-        obj = os.path.join("/tmp", "prof_" + src.replace(".hip", ".o"))
-        # the bench's instance only (KGE_ONLY_ONE): seconds instead of minutes
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DKGE_PHASE_PROF",
-                        "-DKGE_ONLY_ONE"] + list(extra) + ["-c", os.path.join(CSRC, src), "-o", obj], check=True)
-        objs.append(obj)
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB], check=True)
-    print("built", LIB)
+    """The library's objects with the C2 instance (kge_step.hip, which holds the
+    counters, and the plan in kge_abi.hip) recompiled with -DKGE_PHASE_PROF."""
+    from variants import ELEMENTWISE_UNITS, build_lib
+    flags = ["-DKGE_PHASE_PROF", "-DKGE_ONLY_ONE"] + list(extra)
+    build_lib(LIB, "prof", {"kge_step.hip": flags, "kge_abi.hip": flags}, omit=ELEMENTWISE_UNITS)
 
 
 def run(args):

@@ -1,4 +1,5 @@
-"""Score-kernel tuning variants (C2 instance only, -DKGE_ONLY_ONE).
+"""Score-kernel tuning variants (C2 instance only, -DKGE_ONLY_ONE): the library's
+own objects with kge_step.hip and kge_abi.hip recompiled under the knobs.
 
     python tools/variants.py build NAME -DKGE_SLOTS_PER_WAVE=128 ...   # here: KGE/_lib/libkge_var_NAME.so
     python tools/variants.py buildfull NAME -D...   # every model family (all library sources)
@@ -13,34 +14,52 @@ CSRC = os.path.join(ROOT, "knowledge-graph-embedding_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "knowledge-graph-embedding_amd", "KGE", "_lib")
 
 
-def build(name, defines, full=False):
+# kge_step.hip under -DKGE_ONLY_ONE holds the one element-wise instance itself and calls
+# none of these units; linked in, their default-knob copy of that kernel would share its name
+ELEMENTWISE_UNITS = ("kge_step_transe.hip", "kge_step_distmult.hip", "kge_step_rotate.hip")
+
+
+def build_lib(out, tag, recompiled, omit=()):
+    """Link `out` from the objects __graft_entry__.build() made, with the units
+    in `recompiled` ({source: extra flags}) compiled again as build/var/TAG_*.o
+    and those in `omit` left out."""
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as g
+    stock = {src: os.path.join(ROOT, "build", "obj", "%s.%s.o" % (src[:-4], g._obj_key(src)))
+             for src in g.SOURCES if src not in recompiled and src not in omit}
+    if stock:
+        g.build(force=not all(os.path.exists(o) for o in stock.values()))
+    vardir = os.path.join(ROOT, "build", "var")
+    os.makedirs(vardir, exist_ok=True)
     objs, procs = [], []
-    if full:
-        sys.path.insert(0, ROOT)
-        import __graft_entry__
-        sources, defines = __graft_entry__.SOURCES, list(defines)
-    else:
-        sources, defines = ("kge_step.hip", "kge_abi.hip", "kge_transr.hip", "kge_rel.hip", "kge_stream.hip", "kge_exchange.hip",
-                            "kge_owner_transe.hip", "kge_owner_other.hip"), \
-            ["-DKGE_ONLY_ONE"] + list(defines)
-    for src in sources:
-        # single-instance builds: the knobs are the score / update kernels' (kge_step.hip)
-        # and the plan's (kge_abi.hip: KGE_STEP_WAVES, KGE_SLOTS_PER_WAVE size the launch);
-        # the other units are compiled once, shared by every variant
-        shared = not full and src not in ("kge_step.hip", "kge_abi.hip")
-        obj = "/tmp/var_%s_%s" % ("shared" if shared else name, src.replace(".hip", ".o"))
-        if shared and os.path.exists(obj):
-            objs.append(obj)
+    for src in g.SOURCES:
+        if src in omit:
             continue
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + \
-              (["-DKGE_ONLY_ONE"] if shared else defines) + ["-c", os.path.join(CSRC, src), "-o", obj]
-        procs.append(subprocess.Popen(cmd))
+        if src in stock:
+            objs.append(stock[src])
+            continue
+        obj = os.path.join(vardir, "%s_%s.o" % (tag, src[:-4]))
+        procs.append(subprocess.Popen(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] +
+                                      list(recompiled[src]) + ["-c", os.path.join(CSRC, src), "-o", obj]))
         objs.append(obj)
     for p in procs:
         assert p.wait() == 0
-    out = os.path.join(LIBDIR, "libkge_var_%s.so" % name)
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out], check=True)
     print("built", out)
+
+
+def build(name, defines, full=False):
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as g
+    if full:
+        recompiled = {src: list(defines) for src in g.SOURCES}
+    else:
+        # the knobs are the score / update kernels' (kge_step.hip: the C2 instance only)
+        # and the plan's (kge_abi.hip: KGE_STEP_WAVES, KGE_SLOTS_PER_WAVE size the launch,
+        # and it refuses the families whose objects keep the default knobs)
+        recompiled = {src: ["-DKGE_ONLY_ONE"] + list(defines) for src in ("kge_step.hip", "kge_abi.hip")}
+    build_lib(os.path.join(LIBDIR, "libkge_var_%s.so" % name), "var_" + name, recompiled,
+              omit=() if full else ELEMENTWISE_UNITS)
 
 
 def run(names, extra=()):
